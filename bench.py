@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- train images/sec of the ZS3 hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          # N>1: launched by torch.distributed.run
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]     # N>1: launched by torch.distributed.run
+
+A plain run sets up, warms up, times K steps of the workload below and prints the line (with --dump-outputs DIR it first writes what
+the last timed step returned: DIR/<name>.npy).  Everything the headline `value` does not need -- `roofline`, `cpu_baseline` and the
+further objects listed at the end -- runs only with --full.
 
 Workload (config.workload): configs[1] of BASELINE.json -- the supervised DeepLabv3+ ResNet-101 training step of
 train_pascal.py (forward, CE, backward, SGD; base_trainer.py:16-20) on synthetic 513x513 batches, 16 images per GPU,
 21 classes, fp32 semantics computed as three-product 16-bit hi/lo splits on the MFMA cores (forward fp16 halves, backward bf16 halves).  Weak scaling: every rank owns 16 images;
-gradients are SUM all-reduced over RCCL while backward runs (zs3_amd.parallel.GradSync).  The GMMN step
+gradients are SUM all-reduced over RCCL while backward runs (zs3_amd.parallel.GradSync).  With --full the GMMN step
 (configs[2], train_pascal_GMMN.py:139-268) is timed after the main loop and reported under "gmmn".
 
-One JSON line on stdout (rank 0).  `roofline` prices the dominant kernel (the LDS-DMA 256x128 implicit-GEMM convolution)
+One JSON line on stdout (rank 0).  With --full: `roofline` prices the dominant kernel (the LDS-DMA 256x128 implicit-GEMM convolution)
 with HIP events recorded around its launches inside the timed region (every 5th timed step); `cpu_baseline` times the CPU oracle
 (oracle/zs3_oracle, the checked restatement of the reference) on the host cores for a bounded sample.
 
-Further objects of the line, none of them part of `value` (each has a --*-steps flag, 0 = skip): `bf16` (the 2-byte mode of
+Further objects of the --full line, none of them part of `value` (each has a --*-steps flag, 0 = skip): `bf16` (the 2-byte mode of
 configs[4], same process, after the timed loop), `gmmn` (configs[2]; `gmmn.script_loop` = the reference's own per-image x
 per-class loop body driven through the drop-in classes), and, at N = 1 only and in child processes so that they cannot
 disturb the timed loop, `shard` (what ONE rank of the 8-GPU configs[3] run executes: 8 images, 60 classes, no collectives)
@@ -42,6 +46,7 @@ DTYPE_NOTE = {"bf16x3": "x3 split (fp32 operands as 16-bit hi+lo, 3 MFMA product
               "bf16f32": "bf16 products on fp32 storage (plain bf16 MFMA products, fp32 accumulate; every tensor fp32 in HBM)"}
 LAUNCH_BOUNDARY_US = 1.45         # dependent kernel boundary on one stream (MI355X_MICROARCH.md price list)
 PEAK_BF16_TF = 2500.0                                 # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 20             # --dump-outputs: elements kept of a larger output (4 MB as float32)
 
 
 def parse():
@@ -53,7 +58,14 @@ def parse():
     ap.add_argument("--size", type=int, default=513)
     ap.add_argument("--classes", type=int, default=21)
     ap.add_argument("--workload", choices=["supervised", "gmmn", "gcn_context"], default="supervised")
-    ap.add_argument("--gmmn-steps", type=int, default=10, help="timed GMMN steps (configs[2]) after the supervised loop; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline `value` does not need: `cpu_baseline`, `roofline`, `bf16`, `gmmn` (with "
+                         "`script_loop`) and the child runs `shard`, `ddp_one_rank`, `host_batches`.  Without it a run sets up, warms "
+                         "up, times --steps steps and prints the line; the --*-steps flags below then default to 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32 / "
+                         "float64; outputs larger than %d elements as a fixed, seeded sample)" % DUMP_SAMPLE)
+    ap.add_argument("--gmmn-steps", type=int, default=None, help="timed GMMN steps (configs[2]) after the supervised loop; 0 = skip")
     ap.add_argument("--dtype", choices=["bf16x3", "bf16", "bf16f32"], default="bf16x3",
                     help="bf16x3 = fp32 storage, fp32 semantics as three bf16 MFMA products (configs[1-3]); bf16 = the 2-byte mode of "
                          "configs[4]: activations and inter-layer gradients stored as bf16, plain bf16 products, fp32 accumulate / "
@@ -72,26 +84,36 @@ def parse():
                          "section 7 quotes this PCIe-inclusive rate")
     ap.add_argument("--read-loss", type=int, default=1,
                     help="1 (default): every timed step's loss value is read on the host, one step behind (what BaseTrainer does); 0: never")
-    ap.add_argument("--bf16-steps", type=int, default=10,
-                    help="timed steps of the 2-byte mode reported as the `bf16` object of the default line; 0 = skip")
-    ap.add_argument("--shard-steps", type=int, default=10,
+    ap.add_argument("--bf16-steps", type=int, default=None,
+                    help="timed steps of the 2-byte mode reported as the `bf16` object of the --full line; 0 = skip")
+    ap.add_argument("--shard-steps", type=int, default=None,
                     help="timed steps of `shard`: what ONE rank of BASELINE configs[3] runs (B = 8 images, 60 classes); 0 = skip")
-    ap.add_argument("--ddp-steps", type=int, default=10,
+    ap.add_argument("--ddp-steps", type=int, default=None,
                     help="timed steps of `ddp_one_rank`: the supervised step on the N > 1 code path with a one-rank RCCL group and "
                          "SyncBN (gradient buckets, 208 SyncBN all-reduces, global CE), run as a child process; 0 = skip")
-    ap.add_argument("--host-steps", type=int, default=10,
+    ap.add_argument("--host-steps", type=int, default=None,
                     help="timed steps of `host_batches`: the supervised step taking every batch from pinned host memory (54 MB over "
                          "PCIe per step, what base_trainer.py:13 does), child process; 0 = skip")
-    ap.add_argument("--script-steps", type=int, default=3,
+    ap.add_argument("--script-steps", type=int, default=None,
                     help="timed iterations of `gmmn.script_loop`: the reference's own per-image x per-class loop body "
                          "(train_pascal_GMMN.py:139-268) on the drop-in modules; 0 = skip")
     ap.add_argument("--plan", type=int, default=1,
                     help="1 (default): the supervised step runs as a recorded launch plan (zs3_amd/plan.py: recorded once after two eager "
                          "steps, then replayed from C -- bit-identical to the eager step, tests/test_gpu_plan.py); 0: every step eager "
                          "(one Python -> ctypes call per launch).  Instrumented steps (roofline events) are always eager.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without `roofline`")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # the measurements beside the headline run only with --full (an explicit --*-steps value is taken as given)
+    for name, full_default in (("gmmn_steps", 10), ("bf16_steps", 10), ("shard_steps", 10), ("ddp_steps", 10),
+                               ("host_steps", 10), ("script_steps", 3)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.roofline = args.full and not args.no_roofline
+    return args
 
 
 def spawn_ranks(args):
@@ -120,7 +142,7 @@ def main():
         raise SystemExit("bench.py needs an MI355X: the product path has no CPU fallback")
     # the CPU baseline (a child process on the host cores) runs FIRST: the GPU phase that follows is then one contiguous
     # stretch at the end of the run instead of a few seconds hidden in front of a minute of CPU work
-    cpu_info = cpu_baseline(args) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    cpu_info = cpu_baseline(args) if (rank == 0 and world == 1 and args.cpu_baseline) else None
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     # the step's streams take their hardware queues before the process group creates its own (zs3_amd.functional.warm_streams)
@@ -188,6 +210,7 @@ def main():
 
     from zs3_amd.plan import StepPlan
     plan_step = StepPlan(model, crit, opt, enabled=bool(args.plan))
+    last_out = [None]      # the prediction of the latest supervised step (--dump-outputs)
 
     def supervised_step(i, eager=False):
         img, lab = image, label
@@ -201,6 +224,7 @@ def main():
         # zero_grad -> forward -> loss -> backward -> optimizer step (base_trainer.py:16-20): eager for the first two calls of a
         # configuration, recorded on the third, replayed from C afterwards (N > 1: always eager, the collectives are torch.distributed's)
         out, loss = plan_step(img, lab, eager=eager)
+        last_out[0] = out
         # the trainer reads the loss of every iteration (zs3_amd/base_trainer.py; the reference: base_trainer.py:21,24).  Read the way
         # the trainer reads it: copied to pinned host memory behind the step, looked at one iteration later -- every value is read,
         # no step waits for its own
@@ -211,7 +235,9 @@ def main():
     from zs3_amd.base_trainer import LossLog
     loss_log = LossLog(dev) if args.read_loss else None
 
-    def run(step, steps, warmup):
+    def run(step, steps, warmup, first=None):
+        """warmup untimed calls step(0 .. warmup-1), then `steps` timed calls step(first + k); first defaults to warmup"""
+        first = warmup if first is None else first
         for i in range(warmup):
             step(i)
         if world > 1:
@@ -219,7 +245,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(steps):
-            last = step(warmup + i)
+            last = step(first + i)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -325,7 +351,9 @@ def main():
                     break
                 supervised_step(i)
         if not roofline:
-            dt, last = run(supervised_step, steps, warmup)
+            # the step index sets the learning rate: a run that did not say --no-roofline numbers its timed steps from 0 like the
+            # instrumented path below (what such a run computed before --full existed), a --no-roofline run from `warmup`
+            dt, last = run(supervised_step, steps, warmup, first=warmup if args.no_roofline else 0)
             return dt, last, [], [], 0
         # warm-up steps: HIP events around every conv launch (per-kernel table, picks the dominant kernel);
         # timed steps: events around the dominant kernel's launches only -- an event pair is a kernel boundary the
@@ -388,12 +416,14 @@ def main():
 
     bf16_info = None
     if args.workload == "supervised":
-        dt, last, prof, warm_prof, instrumented = measure_supervised(args.steps, args.warmup, not args.no_roofline)
+        dt, last, prof, warm_prof, instrumented = measure_supervised(args.steps, args.warmup, args.roofline)
         # resolve the instrumentation's timing events NOW and let them go: ~500 unread HIP timing events held across the phases below
         # made whichever phase came third 25-35 % slower (shard 35.8 instead of 28 ms, or bf16 39.7 instead of 29.4: the events' signals
         # are a finite pool that the side-stream waits of the weight-gradient launches share)
         roof_main = roofline_of(prof, warm_prof, instrumented, args.dtype) if (rank == 0 and prof) else None
         prof, warm_prof = [], []
+        if args.dump_outputs and rank == 0:     # (before anything else runs on the model or the plan's buffers)
+            dump_outputs(args.dump_outputs, {"loss": last, "logits": last_out[0], "params": model_params(model)})
         inst_replayed = bool(getattr(measure_supervised, "replayed_instrumented", False))
         n_eager = 0 if inst_replayed else instrumented
         executor = {"plan": bool(plan_step.recorded_ops), "recorded_launches": plan_step.recorded_ops,
@@ -406,7 +436,7 @@ def main():
             # the 2-byte mode (BASELINE configs[4] "bf16") on the same model, optimizer and batch: activations and
             # inter-layer gradients stored as bf16, plain bf16 products
             ops.set_storage(torch.bfloat16)
-            bdt, _, bprof, bwarm, binst = measure_supervised(args.bf16_steps, 3, not args.no_roofline)
+            bdt, _, bprof, bwarm, binst = measure_supervised(args.bf16_steps, 3, args.roofline)
             ops.set_storage(torch.float32)      # (a round trip: arithmetic and weight-gradient kernel selection come back)
             bval = args.batch * args.bf16_steps / bdt
             bf16_info = {"value": bval, "unit": "images/sec", "ms_per_step": 1e3 * bdt / args.bf16_steps, "steps": args.bf16_steps,
@@ -431,19 +461,26 @@ def main():
         prof, warm_prof, instrumented, roof_main = [], [], 0, None
         dt, last = run(gstep, args.steps, args.warmup)
         gflop_img = 193.5
+        if args.dump_outputs and rank == 0:
+            # GMMNStep -> (generator loss, classifier loss, logits); GCNContextStep -> (generator loss, GCN loss, classifier loss, logits)
+            names = ("generator_loss", "classifier_loss") if len(last) == 3 else ("generator_loss", "generator_gcn_loss", "classifier_loss")
+            arrays = dict(zip(names, last[:-1]))
+            arrays.update({"logits": last[-1], "params": model_params(model),
+                           "generator_params": model_params(gstep.stepper.generator)})
+            dump_outputs(args.dump_outputs, arrays)
 
     value = world * args.batch * args.steps / dt
     result = {
         "metric": "train images/sec, DeepLabv3+ + GMMN 513x513",
         "value_is": ("the supervised DeepLabv3+ step (BASELINE configs[1], the configuration the metric is quoted on); the +GMMN "
-                     "step (configs[2]) is reported in full under `gmmn`" if args.workload == "supervised" else args.workload + " step"),
+                     "step (configs[2]) is reported in full under `gmmn` (--full)" if args.workload == "supervised" else args.workload + " step"),
         "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         # the last timed step's loss: a dead network (all-zero activations) runs the same kernels 10-45 % faster on this chip (lower
         # switching power, higher clocks: found in round 4), so the line carries the evidence that it was alive
         "last_loss": float(last.detach().float().item()) if torch.is_tensor(last) else (float(last[1]) if isinstance(last, tuple) else None),
         "dtype": DTYPE_NOTE[args.dtype], "data": "synthetic",
-        "config": {"workload": ("train_pascal.py supervised step: DeepLabv3+ ResNet-101 fwd+CE+bwd+SGD (BASELINE configs[1]); the +GMMN step (configs[2]) is the `gmmn` object of this line"
+        "config": {"workload": ("train_pascal.py supervised step: DeepLabv3+ ResNet-101 fwd+CE+bwd+SGD (BASELINE configs[1]); the +GMMN step (configs[2]) is the `gmmn` object of the --full line"
                                 if args.workload == "supervised" else
                                 "train_pascal_GMMN.py step (BASELINE configs[2])" if args.workload == "gmmn" else
                                 "train_context_GMMN_GCNcontext.py step (GCN-context flow of BASELINE configs[4], fp32 arithmetic as above)"),
@@ -494,6 +531,30 @@ def main():
         torch.cuda.synchronize()
         _par.native_shutdown()
         dist.destroy_process_group()
+
+
+def model_params(module):
+    """every parameter of `module` after the step, flattened and concatenated in `parameters()` order"""
+    return torch.cat([p.detach().float().reshape(-1) for p in module.parameters()])
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor or number} -> DIR/<name>.npy, tensors as float32 (float64 stays float64), numbers as float64
+    scalars.  A tensor of more than DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE logical indices drawn from a
+    generator seeded with a constant (sorted; the same positions in every run of the same arguments)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            if v.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(20240601)
+                idx = torch.randint(0, v.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+                v = torch.take(v, idx.to(v.device))
+            a = v.cpu().numpy() if v.dtype == torch.float64 else v.float().cpu().numpy()
+        else:
+            a = np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 

@@ -270,6 +270,33 @@ def test_bench_refuses_to_run_without_the_devices_it_was_asked_for():
     assert r.returncode != 0 and "no CPU fallback" in (r.stderr + r.stdout)
 
 
+def test_bench_measures_only_the_headline_without_full():
+    """A plain `bench.py` run times the workload and nothing else; `--full` brings back every side measurement with its old
+    step counts; an explicit --*-steps value holds either way; --steps 0 is refused (ms_per_step would be undefined)."""
+    import json
+    import subprocess
+    import sys
+    code = ("import json, sys\n"
+            f"sys.path.insert(0, {ROOT!r})\n"
+            "import bench\n"
+            "out = []\n"
+            "for argv in (sys.argv[1].split(), sys.argv[2].split(), sys.argv[3].split()):\n"
+            "    sys.argv = ['bench.py'] + argv\n"
+            "    out.append(vars(bench.parse()))\n"
+            "print(json.dumps(out))\n")
+    r = subprocess.run([sys.executable, "-c", code, "--steps 7 --warmup 2", "--full", "--steps 3 --bf16-steps 4 --dump-outputs d"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    plain, full, mixed = json.loads(r.stdout.strip().splitlines()[-1])
+    side = ("gmmn_steps", "bf16_steps", "shard_steps", "ddp_steps", "host_steps", "script_steps")
+    assert (plain["steps"], plain["warmup"], plain["full"], plain["dump_outputs"]) == (7, 2, False, None)
+    assert all(plain[k] == 0 for k in side) and not plain["cpu_baseline"] and not plain["roofline"]
+    assert [full[k] for k in side] == [10, 10, 10, 10, 10, 3] and full["cpu_baseline"] and full["roofline"]
+    assert (mixed["steps"], mixed["bf16_steps"], mixed["gmmn_steps"], mixed["dump_outputs"]) == (3, 4, 0, "d")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
 def test_io_argument_sits_before_the_stream_on_every_activation_entry_point():
     """Round 4, the 2-byte mode at the C ABI: every entry point whose tensors are activations carries `int io` as its last
     argument before `void* stream` (bit 0: inputs are bf16, bit 1: outputs are); entry points that only see fp32 state
