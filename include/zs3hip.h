@@ -503,7 +503,8 @@ int zs3_plan_get_arg(long plan, int op, int arg, void* out, int cap);
  * long, 'h' host array copied into the plan; 0 behind the last argument */
 int zs3_plan_arg_kind(long plan, int op, int arg);
 /* waiter waits for everything queued on producer so far (event record + stream wait, one reusable event per waiting stream):
- * the cross-stream dependencies of the step (weight-gradient side streams, functional.py) as a recordable call. */
+ * the cross-stream dependencies of the step (weight-gradient side streams, functional.py) as a recordable call.  -> 0, or a HIP
+ * error code (hipErrorInvalidResourceHandle when the wait's event could not be created). */
 int zs3_stream_wait(void* waiter, void* producer);
 
 #ifdef __cplusplus

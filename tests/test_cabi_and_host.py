@@ -469,3 +469,38 @@ def test_plan_entry_points_and_generated_wrappers():
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", L._name], capture_output=True, text=True).stdout
     assert "__impl" not in out
+
+
+def test_plan_guard_sorts_tensor_library_ops():
+    """zs3_amd.plan._TensorLibraryWork, the dispatch mode a recording runs under, on meta tensors: allocations, views and aliases
+    pass; arithmetic, fills, device-to-device copies and _foreach_* are logged, backward's included; a host-to-device copy counts
+    unless its destination is one the caller moves out of the step; work on other devices is not its business."""
+    from zs3_amd.plan import _TensorLibraryWork
+    x = torch.empty(4, 3, device="meta", requires_grad=True)
+    quiet = _TensorLibraryWork("meta")
+    with quiet:
+        a = torch.empty(4, 3, device="meta")
+        a.new_empty((2,))
+        torch.empty_strided((2, 2), (1, 2), device="meta")
+        x.permute(1, 0)
+        x.reshape(-1)
+        x.detach()
+        x[1:]
+        torch.randn(3).mul_(2.0)                             # (CPU work: none of the meta recording's business)
+    assert quiet.unrecorded() == [], quiet.unrecorded()
+    loud = _TensorLibraryWork("meta")
+    with loud:
+        y = x * 2.0
+        y.sum().backward()
+        a.zero_()
+        a.copy_(torch.empty(4, 3, device="meta"))
+        torch._foreach_add_([a], 1.0)
+    ops = loud.unrecorded()
+    assert ops[:2] == ["aten.mul.Tensor", "aten.sum.default"], ops
+    assert "aten.zero_.default" in ops and "aten.copy_.default" in ops and any("_foreach_add" in o for o in ops), ops
+    assert len([o for o in ops if o == "aten.mul.Tensor"]) == 2, ops            # forward and backward
+    up = _TensorLibraryWork("meta")
+    with up:
+        dst = torch.ones(8).to("meta")
+    assert up.ops == [] and len(up.uploads) == 1
+    assert up.unrecorded() == ["aten._to_copy.default"] and up.unrecorded({dst.data_ptr()}) == []

@@ -195,6 +195,83 @@ def test_one_rank_rccl_step_replays_from_a_plan(dev, one_rank_group):
         par.FORCE_COLLECTIVES = False
 
 
+class _ScaledLogits(torch.nn.Module):
+    """DeepLab with a learnable scalar on its logits: the scalar's gradient is made by autograd, not written into its bucket slice"""
+
+    def __init__(self, net):
+        super().__init__()
+        self.net = net
+        self.t = torch.nn.Parameter(torch.full((), 1.25, device=next(net.parameters()).device))
+
+    def forward(self, x):
+        return self.net(x) * self.t
+
+
+def _grad_sync_plan_run(dev, use_plan, variant):
+    """6 steps of a one-rank GradSync(force=True) step through StepPlan: (losses, state_dict, momentum buffers, counters)"""
+    import zs3_amd.parallel as par
+    from zs3_amd import functional as Fz
+    from zs3_amd.modeling.deeplab import DeepLab
+    from zs3_amd.optim import SGD
+    from zs3_amd.parallel import GradSync
+    from zs3_amd.plan import StepPlan
+    from zs3_amd.utils.loss import SegmentationLosses
+    from zs3_amd.utils.synthetic import make_batch
+    torch.manual_seed(1)
+    net = DeepLab(num_classes=21, pretrained=False, sync_bn=False)
+    for name, mod in net.named_modules():
+        if name.endswith("bn3"):
+            mod.weight.data.fill_(0.1)
+    net = net.to(dev).train()
+    model = _ScaledLogits(net) if variant == "scalar" else net
+    groups = [{"params": list(net.get_1x_lr_params()), "lr": 1e-3}, {"params": list(net.get_10x_lr_params()), "lr": 1e-2}]
+    if variant == "scalar":
+        groups[1]["params"].append(model.t)
+    par.FORCE_COLLECTIVES = True
+    sync = GradSync(list(model.parameters()), average=variant == "average", force=True)
+    try:
+        if variant == "unbucketed":
+            # one conv weight whose gradient the layer writes into a tensor of its own: GradSync packs it into the bucket and unpacks
+            # the reduced values with tensor-library copies
+            Fz.register_grad_buffer(net.backbone.layer4[0].conv2.weight, None)
+        opt = SGD(groups, momentum=0.9, weight_decay=5e-4)
+        crit = SegmentationLosses(cuda=True).build_loss("ce")
+        Fz.manual_seed(5)
+        step = StepPlan(model, crit, opt, enabled=use_plan)
+        losses = []
+        for i in range(6):
+            b = make_batch(2, 65, seed=90 + i, device=dev)
+            losses.append(step(b["image"], b["label"])[1].detach().clone())
+        torch.cuda.synchronize()
+        if variant == "in_place":
+            assert all(sync._in_place(p) for p in sync.params if p.grad is not None)
+        out = (torch.stack(losses).cpu(), {k: v.detach().clone() for k, v in model.state_dict().items()},
+               [opt.state[p]["momentum_buffer"].detach().clone() for g in opt.param_groups for p in g["params"]],
+               (step.eager_calls, step.recordings, step.replays), list(step.unrecorded_ops))
+        step.close()
+        return out
+    finally:
+        sync.remove()
+        par.FORCE_COLLECTIVES = False
+
+
+@pytest.mark.parametrize("variant,counts", [("in_place", (2, 1, 3)), ("average", (5, 0, 0)), ("scalar", (5, 0, 0)),
+                                            ("unbucketed", (5, 0, 0))], ids=["in_place", "average", "scalar", "unbucketed"])
+def test_grad_sync_steps_with_tensor_library_work_stay_eager(dev, one_rank_group, variant, counts):
+    """GradSync's own tensor-library work -- the division of average=True, the pack / unpack copies of a gradient that is not its
+    bucket slice -- is not part of a plan: such a step stays eager (2 settling calls, 1 recording attempt that gives up, eager
+    calls) and equals the run without a plan; the in-place SUM configuration records and replays.  With one rank the collective
+    is the identity: this checks the plan's decision, which every rank makes alike."""
+    le, se, me, ce, _ = _grad_sync_plan_run(dev, False, variant)
+    lp, sp, mp, cp, unrecorded = _grad_sync_plan_run(dev, True, variant)
+    print(f"\n[grad sync {variant}] counts {cp}, unrecorded ops {unrecorded[:8]}")
+    assert torch.equal(le, lp), (le, lp)
+    assert not [k for k in se if not torch.equal(se[k], sp[k])]
+    assert all(torch.equal(a, b) for a, b in zip(me, mp))
+    assert ce == (6, 0, 0) and cp == counts, (ce, cp)
+    assert bool(unrecorded) == (counts != (2, 1, 3)), unrecorded
+
+
 def _gmmn_steps(dev, ddp):
     from zs3_amd.gmmn_trainer import GMMNStep
     from zs3_amd.modeling.deeplab import DeepLab

@@ -93,7 +93,7 @@ static hipEvent_t wait_event_of(hipStream_t waiter, hipStream_t producer) {
 static int stream_wait_impl(void* waiter, void* producer) {
   if (waiter == producer) return 0;
   hipEvent_t ev = wait_event_of((hipStream_t)waiter, (hipStream_t)producer);
-  if (!ev) return (int)hipGetLastError();
+  if (!ev) return (int)hipErrorInvalidResourceHandle;   // (no event: hipGetLastError() may read 0 here, and 0 is a wait done)
   hipError_t rc = hipEventRecord(ev, (hipStream_t)producer);
   if (rc != hipSuccess) return (int)rc;
   return (int)hipStreamWaitEvent((hipStream_t)waiter, ev, 0);

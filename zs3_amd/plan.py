@@ -20,25 +20,78 @@ What makes a replay valid, and how it is kept:
 * cross-stream order is part of the plan (zs3_stream_wait); while recording, the ASPP branches run on one stream and
   side-stream operands are kept alive instead of handed to the allocator's record_stream bookkeeping (functional.PLAN_RECORDING);
 * nothing of the step may run outside the library: the tensor-library stragglers of earlier rounds (loss clone, bias-gradient
-  reduction, zero fills, channel pads, the optimizer's per-step table upload for the schedule) are library calls now;
+  reduction, zero fills, channel pads, the optimizer's per-step table upload for the schedule) are library calls now; while a
+  plan records, a dispatch mode (_TensorLibraryWork) logs every op the tensor library runs on device memory, and a step that
+  ran one is not planned (`unrecorded_ops` names them);
 * anything that changes what the step launches drops the plan and the next calls run eagerly / re-record: another input shape
   or dtype, train / eval flips, requires_grad or parameter storage changes, another set of optimizer hyper-parameters than lr and
   weight decay, a precision / storage mode switch or range-guard fallback (functional.PLAN_EPOCH).
 Several ranks: with the RCCL backend the step's collectives are entry points of the library (csrc/comm.hip) on the streams that hold
 the data, so the N > 1 step records and replays like the one-GPU step.  Not planned (the call runs eagerly, every time):
 collectives through torch.distributed (gloo, ZS3_NATIVE_RCCL=0), an optimizer other than zs3_amd.optim.SGD, CPU tensors, gradient
-mode off.
+mode off, a step in which the tensor library launched work (focal loss, torch-op criteria, GradSync with `average=True` or
+gradients outside their bucket).
 """
 import ctypes
 import os
 
 import torch
+from torch.utils._python_dispatch import TorchDispatchMode
+from torch.utils._pytree import tree_leaves
 
 from . import functional as Fz
 from . import ops
 from ._lib import Zs3HipError, check, lib
 
 ENABLED = os.environ.get("ZS3_PLAN", "1") == "1"
+
+# ops of the tensor library that do no device work, by overload packet (besides views, func.is_view):
+_NO_DEVICE_WORK = frozenset((
+    # allocation only: the caching allocator hands out a block, what it holds is up to the launch that writes it next
+    "empty", "empty_like", "empty_strided", "empty_permuted", "new_empty", "new_empty_strided",
+    # aliases that autograd and the layers take of a tensor (not every build flags them as views)
+    "detach", "alias",
+    # bookkeeping of the caching allocator (which streams read a block before it may be reused): it launches nothing
+    # (functional.py hands every weight gradient made on a side stream to the main stream this way, recording or not)
+    "record_stream",
+))
+# host-to-device copies: work a replay does not repeat, allowed only where _record moves the destination out of the step (the
+# optimizer's record tables, checked by pointer after the step)
+_UPLOADS = frozenset(("_to_copy", "copy_"))
+
+
+class _TensorLibraryWork(TorchDispatchMode):
+    """Entered while a plan records: logs every op of the tensor library that touches a tensor on `device_type` and does device
+    work -- fills, arithmetic, device-to-device copies, _foreach_*, .item().  A replay re-issues the library's launches and
+    nothing else, so such an op would be missing from every replayed step (its result stale, the tensor it wrote reused by
+    later launches).  The dispatch-mode stack is part of the thread-local state autograd hands its device threads: the ops of
+    backward, and of its final callbacks (GradSync.finish), are seen too."""
+
+    def __init__(self, device_type="cuda"):
+        super().__init__()
+        self.device_type = device_type
+        self.ops = []            # op names of the unrecorded work, in order
+        self.uploads = []        # (op name, destination pointer) of the host-to-device copies
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        out = func(*args, **(kwargs or {}))
+        leaves = [t for t in tree_leaves((args, kwargs, out)) if isinstance(t, torch.Tensor)]
+        if not any(t.device.type == self.device_type for t in leaves):
+            return out
+        kind = func.overloadpacket.__name__
+        if func.is_view or kind in _NO_DEVICE_WORK:
+            return out
+        if kind in _UPLOADS:
+            dst, src = (args[0], args[1]) if kind == "copy_" else (out, args[0])
+            if dst.device.type == self.device_type and src.device.type == "cpu":
+                self.uploads.append((str(func), dst.data_ptr()))
+                return out
+        self.ops.append(str(func))
+        return out
+
+    def unrecorded(self, moved_ptrs=()):
+        """the unrecorded work: every logged op, and every upload to a destination the caller does not move out of the step"""
+        return self.ops + [name for name, ptr in self.uploads if ptr not in moved_ptrs]
 
 
 def collectives_recordable():
@@ -154,6 +207,7 @@ class StepPlan:
         self.replays = self.recordings = self.eager_calls = 0
         self._one = None
         self._giveup = None          # fingerprint of a configuration whose step turned out not to be replayable
+        self.unrecorded_ops = []     # the tensor library's device work seen by the last recording (non-empty: it gave up)
         self._drop()
         if torch.cuda.is_available():
             Fz.warm_streams()        # (the step's streams take their hardware queues in a fixed order: functional.warm_streams)
@@ -217,13 +271,15 @@ class StepPlan:
             return v
 
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        work = _TensorLibraryWork()
         torch.cuda.synchronize(dev)
         Fz.next_seed, Fz.PLAN_RECORDING = logged_seed, True
         torch._C._cuda_beginAllocateToPool(idx, pool.id)      # every allocation of the step, from either thread, into the pool
         try:
             plan.begin()
             try:
-                prediction, loss = self._eager(image, target)
+                with work:
+                    prediction, loss = self._eager(image, target)
             finally:
                 plan.end()
         except BaseException:
@@ -239,6 +295,12 @@ class StepPlan:
         keep, Fz._plan_keep = Fz._plan_keep, []
         torch.cuda.synchronize(dev)      # the side-stream readers of `keep` are done: from here on stream order on main protects them
         del keep
+        tables = list(getattr(self.optimizer, "_zs3_tables", ()))
+        self.unrecorded_ops = work.unrecorded({t.data_ptr() for t in tables})
+        if self.unrecorded_ops:
+            # the tensor library did device work in the step (a criterion in torch ops, GradSync's pack copies, ...): a replay would
+            # skip it and read what it left in the pool last time -- this configuration stays eager
+            return self._give_up(plan, prediction, loss)
         if len(set(drawn)) != len(drawn):
             plan.close()
             self._settled = 0            # (two equal 63-bit seeds: cannot tell the launches apart; eager now, another recording later)
@@ -252,11 +314,12 @@ class StepPlan:
         while plan.find("zs3_sgd_multi_g", k) >= 0:
             sgd_ops.append(plan.find("zs3_sgd_multi_g", k))
             k += 1
-        for t in getattr(self.optimizer, "_zs3_tables", ()):
-            fixed = t.clone()
+        for t in tables:
             at = [(op, a) for op, a in plan.find_ptr(t.data_ptr()) if op in sgd_ops and a == 0]
             if len(at) != 1:
-                raise RuntimeError("StepPlan: the optimizer's table is not an argument of exactly one recorded optimizer launch")
+                # (the table is not an argument of exactly one recorded optimizer launch: nothing to point at the moved copy)
+                return self._give_up(plan, prediction, loss)
+            fixed = t.clone()
             plan.set_ptr(at[0][0], 0, fixed.data_ptr())
             moved.append(fixed)
         torch.cuda.synchronize(dev)
@@ -268,15 +331,19 @@ class StepPlan:
         if not self._input_at[0] or not self._input_at[1] or image.data_ptr() == target.data_ptr():
             # the step did not read its batch where the caller's tensors live (a cast or a .contiguous() copy the tensor library made
             # in front of the first launch: uint8 / float64 labels, a non-contiguous image): this configuration stays eager
-            plan.close()
-            self._plan, self._pool, self._giveup = None, None, self._key
-            return prediction, loss
+            return self._give_up(plan, prediction, loss)
         self._held = (prediction, loss, moved, image, target)
         self._grads = [(p, p.grad) for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
         self._grads_moved = False
         self._sgd_ops = sgd_ops
         self._hyper = bytes(self.optimizer.group_hyper())
         self.recordings += 1
+        return prediction, loss
+
+    def _give_up(self, plan, prediction, loss):
+        """the recorded step cannot be replayed: drop its plan, keep the configuration eager, hand back the step's eager result"""
+        plan.close()
+        self._plan, self._pool, self._giveup = None, None, self._key
         return prediction, loss
 
     def _replay(self, image, target):
@@ -429,6 +496,7 @@ class ForwardPlan:
         self.warmup = max(2, int(warmup))
         self.enabled = ENABLED if enabled is None else bool(enabled)
         self.replays = self.recordings = self.eager_calls = 0
+        self.unrecorded_ops = []     # the tensor library's device work seen by the last recording (non-empty: it gave up)
         self._plans = {}      # fingerprint (stream included) -> state dict
 
     def _fingerprint(self, image):
@@ -452,7 +520,10 @@ class ForwardPlan:
         if st is None:
             if len(self._plans) > 4:       # (shapes / modes come and go: keep the table small, the pools with it)
                 self.close()
-            st = self._plans[key] = {"seen": 0, "plan": None}
+            st = self._plans[key] = {"seen": 0, "plan": None, "giveup": False}
+        if st["giveup"]:
+            self.eager_calls += 1
+            return self.fn(image)
         if st["plan"] is not None:
             plan = st["plan"]
             if image.data_ptr() != st["input"]:
@@ -482,19 +553,35 @@ class ForwardPlan:
             drawn.append(v)
             return v
 
+        work, pool_id = _TensorLibraryWork(), pool.id
         torch.cuda.synchronize(dev)
         Fz.next_seed, Fz.PLAN_RECORDING = logged_seed, True
-        torch._C._cuda_beginAllocateToPool(idx, pool.id)
+        torch._C._cuda_beginAllocateToPool(idx, pool_id)
         try:
             plan.begin()
             try:
-                out = self.fn(image)
+                with work:
+                    out = self.fn(image)
             finally:
                 plan.end()
+        except BaseException:
+            # the pass itself failed: nothing was recorded that anyone will replay (the plan and the pool go -- the traceback would
+            # keep this frame's references alive); the next calls settle and record again
+            plan.close()
+            del plan, pool
+            torch.cuda.synchronize(dev)
+            Fz._plan_keep.clear()
+            st["seen"] = 0
+            raise
         finally:
-            torch._C._cuda_endAllocateToPool(idx, pool.id)
+            torch._C._cuda_endAllocateToPool(idx, pool_id)
             Fz.next_seed, Fz.PLAN_RECORDING = next_seed, False
         Fz._plan_keep.clear()
+        self.unrecorded_ops = work.unrecorded()
+        if self.unrecorded_ops:
+            plan.close()                   # (the tensor library did device work in the pass: a replay would miss it -- stay eager)
+            st["giveup"] = True
+            return out
         at = plan.find_ptr(image.data_ptr())
         if not at or len(set(drawn)) != len(drawn) or not plan.find_ptr(out.data_ptr()):
             plan.close()                   # (the pass copied its input, or its result is not what a recorded launch wrote: stay eager)
