@@ -244,6 +244,24 @@ int zs3_bilinear_bwd(const float* dout, int ldd, float* dx, int ldo, int N, int 
 int zs3_argmax_confusion(const float* x, int ldx, int N, int H, int W, int C, const void* target, int target_is_i64,
                          int Ho, int Wo, void* conf, void* stream);
 
+/* One validation batch of Trainer.validation (train_pascal.py:125-134, train_pascal_GMMN.py:337-375) from the LOW-resolution
+ * class scores, in one pass over the target pixels and without the resized logits ever existing.  scores: fp32 [N,H,W,C], row
+ * stride ld (fp32 in both storage modes: no `io`); target: float32 or int64 [N,Ho,Wo].  Per target pixel the C scores are
+ * sampled with the align_corners=True arithmetic of zs3_bilinear_fwd (H == Ho samples exactly); from them:
+ *   conf[gt*C + pred] += 1         as zs3_argmax_confusion (first maximum, 0 <= gt < C, int64 counters, accumulated);
+ *   loss_ws = {loss, sum w, sum w*nll}   the weighted CE of SegmentationLosses.CrossEntropyLoss (loss.py:31-46) with the
+ *                                  per-pixel arithmetic and the layout of zs3_ce_fwd; batch = B for batch_average, 0 for
+ *                                  none; weight may be null;
+ *   totals[0] += (double)loss_ws[0]; totals[1] += 1     the device-side `test_loss += loss.item()` (null = skip);
+ *   class_pixels[n*C + c] = pixels of image n with gt == c      (int32 [N,C], overwritten per call; null = skip): the
+ *                                  scripts' per-batch `(target == idx_unseen_class).nonzero()` test without a sync per class.
+ * partial_ws: zs3_val_ws_doubles() doubles (per-block loss sums, reduced in a fixed order: bit-reproducible run to run).
+ * C <= 128; -1 on bad arguments (nothing is launched). */
+int zs3_val_ws_doubles(void);
+int zs3_val_ce_confusion(const float* scores, int ld, int N, int H, int W, int C, const void* target, int target_is_i64,
+                         int Ho, int Wo, const float* weight, int ignore_index, int batch, void* conf, int* class_pixels,
+                         double* partial_ws, float* loss_ws, double* totals, void* stream);
+
 /* ---- losses (loss.hip) ------------------------------------------------------------------------ */
 /* SegmentationLosses.CrossEntropyLoss (zs3/utils/loss.py:31-46): logits [P][ld] (P = B*H*W pixels, C classes),
  * target float32 or int64 [P]; loss_ws (3 floats) = {loss, sum of weights, sum of w*nll}; partial_ws: zs3_ce_ws_doubles()

@@ -384,3 +384,239 @@ extern "C" int zs3_argmax_confusion(const float* x, int ldx, int N, int H, int W
                        (const float*)target, (unsigned long long*)conf);
   return ZS3_LAUNCH_CHECK();
 }
+
+// ------------------------------------------------------------------------------------------------ fused validation step
+// Trainer.validation's per-batch tail (train_pascal.py:125-134, train_pascal_GMMN.py:337-375) from the LOW-resolution class
+// scores in one pass: per target pixel the C scores are sampled with src_index / bilerp (the values zs3_bilinear_fwd would
+// store), and from them come the confusion count of argmax_confusion_kernel, the weighted-CE terms of ce_tile_kernel
+// (loss.hip: fp32 max / expf sum / logf, products accumulated in double) and the per-image class pixel counts.  The
+// [N, Ho, Wo, C] logits never exist.
+// A workgroup owns VT_H x VT_W target pixels at a time (one per thread) and stages the source patch those pixels sample --
+// (8/4 + 2) x (32/4 + 2) pixels at the x4 ratio -- in LDS once, pixel stride C | 1 (odd: conflict-free across source pixels);
+// each thread then walks the classes three times over LDS (argmax + max, exp sum, the target's score) instead of keeping C
+// values in registers.  A tile whose patch does not fit (large C at ratio 1, downsampling) reads global memory directly.
+// Tiles are dealt to blocks in contiguous runs, so a block changes image at most a few times: the class counts of an image
+// are flushed when it does.  Loss sums: one (sum w*nll, sum w) pair of doubles per block, reduced in a fixed order by
+// val_finalize_kernel -- no floating-point atomics, bit-reproducible.
+constexpr int VT_H = 8, VT_W = 32;
+constexpr int VAL_MAX_BLOCKS = 2048;
+
+struct ValArgs {
+  ResizeArgs r;
+  const float* weight;
+  unsigned long long* conf;
+  int* class_pixels;
+  double* partial;
+  int ignore_index, patch_cap;   // patch_cap: floats of LDS behind the histograms (0 = never stage)
+  int tiles_h, tiles_w, tiles, tiles_per_block;
+};
+
+// the C sampled scores of one pixel -> first argmax, and for a pixel the criterion counts its nll
+template <bool CE>
+__device__ __forceinline__ void val_pixel(const float* q00, const float* q01, const float* q10, const float* q11, float w00,
+                                          float w01, float w10, float w11, int C, int t, int& best, float& nll) {
+  best = 0;
+  float bv = bilerp(w00, w01, w10, w11, q00[0], q01[0], q10[0], q11[0]);
+  float mx = bv;
+  for (int c = 1; c < C; ++c) {
+    const float v = bilerp(w00, w01, w10, w11, q00[c], q01[c], q10[c], q11[c]);
+    if (v > bv) {
+      bv = v;
+      best = c;
+    }
+    mx = fmaxf(mx, v);
+  }
+  if (CE) {
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(bilerp(w00, w01, w10, w11, q00[c], q01[c], q10[c], q11[c]) - mx);
+    const float zt = bilerp(w00, w01, w10, w11, q00[t], q01[t], q10[t], q11[t]);
+    nll = (mx + logf(se)) - zt;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void val_ce_confusion_kernel(const ValArgs a, const T* target) {
+  extern __shared__ unsigned val_lds[];
+  const ResizeArgs& p = a.r;
+  const int C = p.C, nbin = C * C, CP = C | 1;
+  unsigned* const hist = val_lds;                                  // [C*C] confusion counts of this block
+  unsigned* const cls = val_lds + nbin;                            // [C] class pixel counts of the current image
+  float* const patch = reinterpret_cast<float*>(val_lds + nbin + C);
+  for (int i = threadIdx.x; i < nbin + C; i += 256) val_lds[i] = 0u;
+  __syncthreads();
+  const int t0 = blockIdx.x * a.tiles_per_block;
+  const int t1 = min(t0 + a.tiles_per_block, a.tiles);
+  const int per_img = a.tiles_h * a.tiles_w;
+  const int ty = threadIdx.x / VT_W, tx = threadIdx.x % VT_W;
+  double lsum = 0.0, wsum = 0.0;
+  int cur_n = t0 < t1 ? t0 / per_img : 0;
+  for (int tile = t0; tile < t1; ++tile) {
+    const int n = tile / per_img, rem = tile - n * per_img;
+    const int r0 = (rem / a.tiles_w) * VT_H, c0 = (rem % a.tiles_w) * VT_W;
+    if (n != cur_n) {   // (block-uniform) the block moves on to another image: hand in the counts of the one it leaves
+      __syncthreads();
+      if (a.class_pixels)
+        for (int i = threadIdx.x; i < C; i += 256)
+          if (cls[i]) atomicAdd(&a.class_pixels[cur_n * C + i], (int)cls[i]);
+      __syncthreads();
+      for (int i = threadIdx.x; i < C; i += 256) cls[i] = 0u;
+      cur_n = n;
+    }
+    // source patch of the tile: rows [ph0, ph1], columns [pw0, pw1] (src_index is monotone in the target coordinate)
+    int ph0, ph1, pw0, pw1, tmp;
+    float ftmp;
+    src_index(r0, p.sh, p.H, ph0, tmp, ftmp);
+    src_index(min(r0 + VT_H, p.Ho) - 1, p.sh, p.H, tmp, ph1, ftmp);
+    src_index(c0, p.sw, p.W, pw0, tmp, ftmp);
+    src_index(min(c0 + VT_W, p.Wo) - 1, p.sw, p.W, tmp, pw1, ftmp);
+    const int ph = ph1 - ph0 + 1, pw = pw1 - pw0 + 1;
+    const bool staged = (long)ph * pw * CP <= (long)a.patch_cap;
+    const float* const img = p.x + (long)n * p.H * p.W * p.ldx;
+    __syncthreads();   // the previous tile's readers are done with the patch (and the cls reset above is visible)
+    if (staged) {
+      const int rowf = pw * C;
+      for (int e = threadIdx.x; e < ph * rowf; e += 256) {
+        const int r = e / rowf, j = e - r * rowf, px = j / C, c = j - px * C;
+        patch[(r * pw + px) * CP + c] = img[((long)(ph0 + r) * p.W + pw0 + px) * p.ldx + c];
+      }
+      __syncthreads();
+    }
+    const int oh = r0 + ty, ow = c0 + tx;
+    if (oh < p.Ho && ow < p.Wo) {
+      const long m = ((long)n * p.Ho + oh) * p.Wo + ow;
+      const T tv = target[m];
+      const double gtd = (double)tv;                       // the evaluator's reading of a label (argmax_confusion_kernel)
+      const bool counted = gtd >= 0.0 && gtd < (double)C;
+      const int t = (int)(long)tv;                         // the criterion's (loss.hip: load_target)
+      const bool valid = !(t == a.ignore_index || t < 0 || t >= C);
+      if (counted || valid) {
+        int h0, h1, w0, w1;
+        float lh, lw;
+        src_index(oh, p.sh, p.H, h0, h1, lh);
+        src_index(ow, p.sw, p.W, w0, w1, lw);
+        const float w00 = (1.f - lh) * (1.f - lw), w01 = (1.f - lh) * lw, w10 = lh * (1.f - lw), w11 = lh * lw;
+        int best;
+        float nll = 0.f;
+        if (staged) {
+          const float* q00 = patch + ((h0 - ph0) * pw + (w0 - pw0)) * CP;
+          const float* q01 = patch + ((h0 - ph0) * pw + (w1 - pw0)) * CP;
+          const float* q10 = patch + ((h1 - ph0) * pw + (w0 - pw0)) * CP;
+          const float* q11 = patch + ((h1 - ph0) * pw + (w1 - pw0)) * CP;
+          if (valid) val_pixel<true>(q00, q01, q10, q11, w00, w01, w10, w11, C, t, best, nll);
+          else val_pixel<false>(q00, q01, q10, q11, w00, w01, w10, w11, C, 0, best, nll);
+        } else {
+          const float* q00 = img + ((long)h0 * p.W + w0) * p.ldx;
+          const float* q01 = img + ((long)h0 * p.W + w1) * p.ldx;
+          const float* q10 = img + ((long)h1 * p.W + w0) * p.ldx;
+          const float* q11 = img + ((long)h1 * p.W + w1) * p.ldx;
+          if (valid) val_pixel<true>(q00, q01, q10, q11, w00, w01, w10, w11, C, t, best, nll);
+          else val_pixel<false>(q00, q01, q10, q11, w00, w01, w10, w11, C, 0, best, nll);
+        }
+        if (counted) {
+          const int gt = (int)gtd;   // astype(int) truncation of metrics.py:75
+          atomicAdd(&hist[gt * C + best], 1u);
+          atomicAdd(&cls[gt], 1u);
+        }
+        if (valid) {
+          const float w = a.weight ? a.weight[t] : 1.f;
+          lsum += (double)(w * nll);
+          wsum += (double)w;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nbin; i += 256)
+    if (hist[i]) atomicAdd(&a.conf[i], (unsigned long long)hist[i]);
+  if (a.class_pixels && t0 < t1)
+    for (int i = threadIdx.x; i < C; i += 256)
+      if (cls[i]) atomicAdd(&a.class_pixels[cur_n * C + i], (int)cls[i]);
+  __shared__ double red[2][4];
+  lsum = wave_sum_d(lsum);
+  wsum = wave_sum_d(wsum);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = lsum;
+    red[1][threadIdx.x >> 6] = wsum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.partial[2 * blockIdx.x + 0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    a.partial[2 * blockIdx.x + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  }
+}
+
+__global__ void val_zero_kernel(int* v, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) v[i] = 0;
+}
+
+// loss_ws as ce_finalize_kernel (loss.hip) leaves it, then the device-side `test_loss += loss.item()`
+__global__ void val_finalize_kernel(const double* partial, int nblk, float inv_batch, float* out, double* totals) {
+  double l = 0.0, w = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 64) {
+    l += partial[2 * k];
+    w += partial[2 * k + 1];
+  }
+  l = wave_sum_d(l);
+  w = wave_sum_d(w);
+  if (threadIdx.x == 0) {
+    const float loss = (float)(l / w) * inv_batch;
+    out[0] = loss;
+    out[1] = (float)w;
+    out[2] = (float)l;
+    if (totals) {
+      totals[0] += (double)loss;
+      totals[1] += 1.0;
+    }
+  }
+}
+
+// rows (or columns) of the source a run of `span` target rows can touch: floor(scale * (span - 1)) + 1 first-rows, one more for the
+// second row of the last, one more for rounding of the fp32 products -- an upper bound (the kernel checks every tile against it)
+static int val_patch_extent(float scale, int span, int in) {
+  const long e = (long)(scale * (float)(span - 1)) + 3;
+  return (int)(e < in ? e : in);
+}
+
+extern "C" int zs3_val_ws_doubles(void) { return 2 * VAL_MAX_BLOCKS; }
+
+extern "C" int zs3_val_ce_confusion(const float* scores, int ld, int N, int H, int W, int C, const void* target,
+                                    int target_is_i64, int Ho, int Wo, const float* weight, int ignore_index, int batch,
+                                    void* conf, int* class_pixels, double* partial_ws, float* loss_ws, double* totals,
+                                    void* stream) {
+  if (C < 1 || C > 128 || N < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || ld < C) return -1;
+  if (!scores || !target || !conf || !partial_ws || !loss_ws) return -1;
+  ValArgs a;
+  a.r = make_resize(scores, ld, nullptr, 0, N, H, W, Ho, Wo, C, 0);
+  a.weight = weight;
+  a.conf = (unsigned long long*)conf;
+  a.class_pixels = class_pixels;
+  a.partial = partial_ws;
+  a.ignore_index = ignore_index;
+  a.tiles_h = (Ho + VT_H - 1) / VT_H;
+  a.tiles_w = (Wo + VT_W - 1) / VT_W;
+  const long tiles = (long)N * a.tiles_h * a.tiles_w;
+  if (tiles >= (1L << 31) || (long)N * C >= (1L << 31)) return -1;
+  a.tiles = (int)tiles;
+  const int blocks = (int)(tiles < VAL_MAX_BLOCKS ? tiles : VAL_MAX_BLOCKS);
+  a.tiles_per_block = (int)((tiles + blocks - 1) / blocks);
+  const int nblk = (int)((tiles + a.tiles_per_block - 1) / a.tiles_per_block);   // blocks that own at least one tile
+  const size_t fixed = ((size_t)C * C + C) * sizeof(unsigned);
+  const size_t want = (size_t)val_patch_extent(a.r.sh, VT_H, H) * val_patch_extent(a.r.sw, VT_W, W) * (C | 1) * sizeof(float);
+  const size_t budget = 64 * 1024 - 128;    // (dynamic part; `red` is static)
+  a.patch_cap = fixed + want <= budget ? (int)(want / sizeof(float)) : 0;
+  const size_t lds = fixed + (size_t)a.patch_cap * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  if (lds > budget) {   // C > ~126: the histogram alone is past the default limit
+    const void* fn = target_is_i64 ? reinterpret_cast<const void*>(&val_ce_confusion_kernel<long>)
+                                   : reinterpret_cast<const void*>(&val_ce_confusion_kernel<float>);
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 128) != hipSuccess) return -4;
+  }
+  if (class_pixels) hipLaunchKernelGGL(val_zero_kernel, dim3((N * C + 255) / 256 > 64 ? 64 : (N * C + 255) / 256), dim3(256), 0, st, class_pixels, N * C);
+  if (target_is_i64)
+    hipLaunchKernelGGL(val_ce_confusion_kernel<long>, dim3(nblk), dim3(256), lds, st, a, (const long*)target);
+  else
+    hipLaunchKernelGGL(val_ce_confusion_kernel<float>, dim3(nblk), dim3(256), lds, st, a, (const float*)target);
+  hipLaunchKernelGGL(val_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)partial_ws, nblk,
+                     batch > 0 ? 1.f / (float)batch : 1.f, loss_ws, totals);
+  return ZS3_LAUNCH_CHECK();
+}

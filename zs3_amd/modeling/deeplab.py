@@ -65,6 +65,12 @@ class DeepLab(nn.Module):
         features = self.decoder.features_nhwc(context, low)
         return self._logits_to_image(self.decoder.predict_nhwc(features), input.shape[2:])
 
+    def forward_scores(self, input):
+        """The class scores of `forward` BEFORE the resize to image size: fp32 [B, h, w, C] in NHWC (not in the reference; what
+        zs3_amd.validation and Evaluator.add_batch_scores consume, so that the full-resolution logits need not exist)."""
+        context, low = self._encode(input)
+        return self.decoder.predict_nhwc(self.decoder.features_nhwc(context, low))
+
     def forward_before_class_prediction(self, input):
         context, low = self._encode(input)
         return ops.nchw(self.decoder.features_nhwc(context, low))

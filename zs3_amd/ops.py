@@ -794,6 +794,40 @@ def bilinear_bwd(dout, in_hw, out=None, accumulate=False):
     return out
 
 
+def val_ws(device):
+    """workspace of val_ce_confusion: the per-block loss sums (zs3_val_ws_doubles() doubles)"""
+    return torch.empty(lib().zs3_val_ws_doubles(), dtype=torch.float64, device=device)
+
+
+def val_ce_confusion(scores, target, conf, weight=None, ignore_index=255, batch=0, class_pixels=None, partial_ws=None,
+                     loss_ws=None, totals=None):
+    """One validation batch from low-resolution class scores (zs3_val_ce_confusion): scores fp32 [N, h, w, C] (NHWC, pixel stride
+    >= C), target float32 / int64 [N, H, W], conf int64 [C, C] (accumulated), weight fp32 [C] or None, class_pixels int32 [N, C]
+    or None (overwritten), totals float64 [2] or None (accumulated: sum of losses, number of batches).  -> loss_ws, fp32 [3] =
+    {loss, sum w, sum w * nll}.  Nothing here synchronises or launches outside the library."""
+    require_gpu(scores, target, conf, weight, class_pixels, partial_ws, loss_ws, totals)
+    n, h, w_, c = scores.shape
+    if scores.dtype != torch.float32 or target.dtype not in (torch.float32, torch.int64) or not target.is_contiguous():
+        raise TypeError("val_ce_confusion: fp32 scores and a contiguous float32 / int64 target")
+    if target.dim() != 3 or target.shape[0] != n or conf.dtype != torch.int64 or conf.numel() != c * c:
+        raise ValueError("val_ce_confusion: target [N, H, W] and int64 [C, C] counters expected")
+    if class_pixels is not None and (class_pixels.dtype != torch.int32 or class_pixels.numel() != n * c):
+        raise ValueError("val_ce_confusion: class_pixels is int32 [N, C]")
+    if totals is not None and (totals.dtype != torch.float64 or totals.numel() != 2):
+        raise ValueError("val_ce_confusion: totals is float64 [2]")
+    if weight is not None and (weight.dtype != torch.float32 or weight.numel() != c or not weight.is_contiguous()):
+        raise ValueError("val_ce_confusion: weight is a dense fp32 [C] tensor")
+    if partial_ws is None:
+        partial_ws = val_ws(scores.device)
+    if loss_ws is None:
+        loss_ws = torch.empty(3, dtype=torch.float32, device=scores.device)
+    check(lib().zs3_val_ce_confusion(P(scores), I(_check_nhwc(scores)), I(n), I(h), I(w_), I(c), P(target),
+                                     I(int(target.dtype == torch.int64)), I(target.shape[1]), I(target.shape[2]), P(weight),
+                                     I(ignore_index), I(batch), P(conf), P(class_pixels), P(partial_ws), P(loss_ws), P(totals),
+                                     stream()), "zs3_val_ce_confusion")
+    return loss_ws
+
+
 # ------------------------------------------------------------------------------------------- misc
 def dropout(x, p, seed, out=None, row_idx=None, seed_dev=None):
     m, c, ld = _rows(x)

@@ -196,6 +196,29 @@ class LaunchPlan:
             pass
 
 
+def poison_pool(pool, dev):
+    """fill every free block of a plan's private pool with 0xFF bytes (NaNs as fp32 and as bf16): what a replay reads without having
+    written it first then shows up instead of finding the last call's bytes (StepPlan.verify, ValidationStep.verify)"""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    torch.cuda.synchronize(dev)
+    free = []
+    for seg in torch.cuda.memory_snapshot():
+        if seg.get("device") != idx or tuple(seg.get("segment_pool_id", (0, 0))) != tuple(pool.id):
+            continue
+        free.extend(b["size"] for b in seg["blocks"] if b["state"] == "inactive")
+    torch._C._cuda_beginAllocateToPool(idx, pool.id)
+    try:
+        hold = []
+        for size in sorted(free, reverse=True):
+            t = torch.empty(size, dtype=torch.uint8, device=dev)
+            t.fill_(255)
+            hold.append(t)
+        torch.cuda.synchronize(dev)
+        del hold
+    finally:
+        torch._C._cuda_endAllocateToPool(idx, pool.id)
+
+
 class StepPlan:
     """See the module docstring.  `warmup`: eager calls before the recording (weight planes, momentum buffers, kernel choices and
     the optimizer's block maps exist and are final after two)."""
@@ -442,25 +465,7 @@ class StepPlan:
 
     def _poison(self):
         """fill every free block of the plan's pool with 0xFF bytes (NaNs as fp32 and as bf16)"""
-        dev = self._held[1].device
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        torch.cuda.synchronize(dev)
-        free = []
-        for seg in torch.cuda.memory_snapshot():
-            if seg.get("device") != idx or tuple(seg.get("segment_pool_id", (0, 0))) != tuple(self._pool.id):
-                continue
-            free.extend(b["size"] for b in seg["blocks"] if b["state"] == "inactive")
-        torch._C._cuda_beginAllocateToPool(idx, self._pool.id)
-        try:
-            hold = []
-            for size in sorted(free, reverse=True):
-                t = torch.empty(size, dtype=torch.uint8, device=dev)
-                t.fill_(255)
-                hold.append(t)
-            torch.cuda.synchronize(dev)
-            del hold
-        finally:
-            torch._C._cuda_endAllocateToPool(idx, self._pool.id)
+        poison_pool(self._pool, self._held[1].device)
 
     def conv_ops(self):
         """indices of the recorded convolution launches (forward and data gradient), in launch order -- the order ops.PROFILE lists

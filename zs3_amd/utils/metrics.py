@@ -129,6 +129,19 @@ class Evaluator:
         check(lib().zs3_argmax_confusion(P(x), I(ld), I(b), I(h), I(w), I(c), P(gt), I(int(gt.dtype == torch.int64)),
                                          I(gt.shape[1]), I(gt.shape[2]), P(conf), stream()), "zs3_argmax_confusion")
 
+    def add_batch_scores(self, gt_image, scores, weight=None, ignore_index=255, batch_average=True, class_pixels=None,
+                         partial_ws=None, loss_ws=None, totals=None):
+        """gt_image: [B, H, W] labels (float32 or int64); scores: fp32 [B, h, w, C] class scores in NHWC, as
+        `DeepLab.forward_scores` returns them (low resolution, or (h, w) == (H, W)).  One fused launch counts the confusion
+        matrix like `add_batch_logits` AND evaluates the validation criterion (weighted CE, zs3_val_ce_confusion) on the
+        resized scores, which never exist.  -> loss_ws, fp32 [3] on the device = {loss, sum w, sum w * nll}; see
+        ops.val_ce_confusion for the optional outputs.  No host synchronisation."""
+        from .. import ops
+        b, h, w, c = scores.shape
+        assert c == self.num_class and gt_image.shape[0] == b and gt_image.dim() == 3
+        return ops.val_ce_confusion(scores, gt_image, self._device_counters(scores.device), weight, ignore_index,
+                                    b if batch_average else 0, class_pixels, partial_ws, loss_ws, totals)
+
     def reset(self):
         self._host = np.zeros((self.num_class,) * 2)
         if self._dev is not None:
