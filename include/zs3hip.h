@@ -262,6 +262,37 @@ int zs3_val_ce_confusion(const float* scores, int ld, int N, int H, int W, int C
                          int Ho, int Wo, const float* weight, int ignore_index, int batch, void* conf, int* class_pixels,
                          double* partial_ws, float* loss_ws, double* totals, void* stream);
 
+/* Pseudo-labels for self-training (ZS5): the producer of the label maps that the data sets read with weak_label=True
+ * (dataloaders/datasets/pascal.py:87-98, sbd.py:103-111, context.py:134-142 -- `weak_label_..._top_by_image_25.0/`), for
+ * which the reference ships no program.  scores: fp32 [N,H,W,C], pixel stride ld; target: float32 or int64 [N,Ho,Wo].
+ * Candidate and unlabelled class sets travel as 128-bit masks (bit c of lo / bit c - 64 of hi); candidates are < C.
+ * A pixel is ELIGIBLE when its label, read as (int)(long)t, is not ignore_index and is in the unlabelled mask or equals
+ * unlabelled_value (< 0: no such value).  Per eligible pixel the C scores are sampled with the align_corners=True arithmetic
+ * of zs3_bilinear_fwd; c* = first argmax over the candidates, conf = softmax over ALL classes at c* (fp32).
+ *   cls_map  uint8 [N,Ho,Wo]   c*, 255 where not eligible
+ *   conf_map fp32  [N,Ho,Wo]   conf, 0 where not eligible
+ *   count    int32 [N,C]       eligible pixels of image n with c* == c (overwritten per call)
+ * C <= 128; -1 on bad arguments (nothing is launched). */
+int zs3_pl_candidates(const float* scores, int ld, int N, int H, int W, int C, const void* target, int target_is_i64,
+                      int Ho, int Wo, unsigned long long cand_lo, unsigned long long cand_hi, unsigned long long unl_lo,
+                      unsigned long long unl_hi, int unlabelled_value, int ignore_index, unsigned char* cls_map,
+                      float* conf_map, int* count, void* stream);
+/* The top-p % selection on the maps of zs3_pl_candidates (the "top_by_image_25.0" of pascal.py:93, 75 % on Context,
+ * context.py:138).  group 0: a bucket is (image, c*); group 1: a bucket is the image.  For a bucket of m eligible pixels
+ * k = min(m, ceil(m * top_percent / 100)) in double; k = 0 keeps nothing, otherwise t = the k-th largest conf of the bucket
+ * (exact: radix select on the bit pattern) and a pixel is kept iff conf >= t -- ties at t are all kept.
+ *   labels    same type and shape as target: target where not eligible, c* where kept, ignore_index otherwise
+ *   selected  int32 [N,C]   kept pixels per image and class (overwritten)
+ *   threshold fp32  [N,C]   t of the bucket the class belongs to (group 1: the same in every candidate column); 0 where k = 0
+ *   totals    int64 [2,C]   [0][c] += sum_n count[n][c], [1][c] += sum_n selected[n][c]: running sums over calls (null = skip)
+ * ws: zs3_pl_ws_bytes(N, C) bytes, 16-byte aligned, cleared by the call.  No host synchronisation; integer atomics only:
+ * the result is independent of launch geometry and bit-reproducible.  -1 on bad arguments (nothing is launched). */
+long zs3_pl_ws_bytes(int N, int C);
+int zs3_pl_select(const float* conf_map, const unsigned char* cls_map, const void* target, int target_is_i64, int N, int Ho,
+                  int Wo, int C, unsigned long long cand_lo, unsigned long long cand_hi, const int* count,
+                  double top_percent, int group, int ignore_index, void* labels, int* selected, float* threshold,
+                  void* totals, void* ws, void* stream);
+
 /* ---- losses (loss.hip) ------------------------------------------------------------------------ */
 /* SegmentationLosses.CrossEntropyLoss (zs3/utils/loss.py:31-46): logits [P][ld] (P = B*H*W pixels, C classes),
  * target float32 or int64 [P]; loss_ws (3 floats) = {loss, sum of weights, sum of w*nll}; partial_ws: zs3_ce_ws_doubles()

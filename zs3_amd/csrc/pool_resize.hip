@@ -620,3 +620,403 @@ extern "C" int zs3_val_ce_confusion(const float* scores, int ld, int N, int H, i
                      batch > 0 ? 1.f / (float)batch : 1.f, loss_ws, totals);
   return ZS3_LAUNCH_CHECK();
 }
+
+// ------------------------------------------------------------------------------------------------ pseudo-labelling (ZS5)
+// The producer of the label maps that the reference's data sets read with weak_label=True (dataloaders/datasets/pascal.py:87-98,
+// sbd.py:103-111, context.py:134-142) and for which it ships no program: the model's own prediction on the pixels whose label
+// is one of the `unlabelled` classes, kept where it is among the top p % most confident of its bucket -- (image, predicted
+// class) or (image).  Two entry points:
+//   zs3_pl_candidates  one pass over the target pixels like val_ce_confusion_kernel (same tiles, same LDS patch, same
+//                      src_index / bilerp samples): per ELIGIBLE pixel the first argmax over the candidate classes and its
+//                      full-softmax probability; cls_map (255 = not eligible), conf_map, per-image class counts.  A tile
+//                      without an eligible pixel stages nothing, a pixel that is not eligible samples nothing.
+//   zs3_pl_select      the exact k-th largest confidence of every bucket by radix select on the BIT PATTERN of conf (a
+//                      non-negative float orders like its uint32 bits): four passes of 8 bits, most significant first.  A pass is
+//                      a histogram kernel (block-private LDS histograms per candidate class, integer atomics into the workspace)
+//                      and a per-bucket scan (one wave per bucket) that picks the digit holding rank k, narrows the prefix and
+//                      the remaining rank and clears the histogram for the next pass.  k = min(m, ceil(m * p / 100)) is computed
+//                      by the first scan from `count`.  The last pass writes labels / selected / threshold: a pixel is kept
+//                      iff conf >= t (ties at t are all kept).  Integer counts only: the result does not depend on the launch
+//                      geometry or on the order of the atomics.
+struct PlArgs {
+  ResizeArgs r;
+  unsigned long long cand_lo, cand_hi, unl_lo, unl_hi;
+  unsigned char* cls_map;
+  float* conf_map;
+  int* count;
+  int unl_value, ignore_index, patch_cap;   // unl_value < 0: none
+  int tiles_h, tiles_w, tiles, tiles_per_block;
+};
+
+__device__ __forceinline__ bool pl_in_mask(unsigned long long lo, unsigned long long hi, int c) {
+  return c >= 0 && c < 128 && (((c < 64 ? lo : hi) >> (c & 63)) & 1ull);
+}
+// rank of class c among the set bits of the mask
+__device__ __forceinline__ int pl_slot(unsigned long long lo, unsigned long long hi, int c) {
+  return c < 64 ? __popcll(lo & ((1ull << c) - 1ull)) : __popcll(lo) + __popcll(hi & ((1ull << (c - 64)) - 1ull));
+}
+
+// the C sampled scores of one pixel -> first argmax over the candidate classes and its probability under the softmax over
+// ALL classes (fp32, the arithmetic of val_pixel: max, expf sum)
+__device__ __forceinline__ void pl_pixel(const float* q00, const float* q01, const float* q10, const float* q11, float w00,
+                                         float w01, float w10, float w11, int C, unsigned long long lo,
+                                         unsigned long long hi, int& best, float& conf) {
+  best = -1;
+  float bv = 0.f, mx = bilerp(w00, w01, w10, w11, q00[0], q01[0], q10[0], q11[0]);
+  for (int c = 0; c < C; ++c) {
+    const float v = bilerp(w00, w01, w10, w11, q00[c], q01[c], q10[c], q11[c]);
+    mx = fmaxf(mx, v);
+    if (pl_in_mask(lo, hi, c) && (best < 0 || v > bv)) {
+      bv = v;
+      best = c;
+    }
+  }
+  float se = 0.f;
+  for (int c = 0; c < C; ++c) se += expf(bilerp(w00, w01, w10, w11, q00[c], q01[c], q10[c], q11[c]) - mx);
+  conf = expf(bv - mx) / se;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pl_candidates_kernel(const PlArgs a, const T* target) {
+  extern __shared__ unsigned pl_lds[];
+  const ResizeArgs& p = a.r;
+  const int C = p.C, CP = C | 1;
+  unsigned* const cls = pl_lds;                                     // [C] eligible pixels per predicted class, current image
+  float* const patch = reinterpret_cast<float*>(pl_lds + C);
+  for (int i = threadIdx.x; i < C; i += 256) cls[i] = 0u;
+  const int t0 = blockIdx.x * a.tiles_per_block;
+  const int t1 = min(t0 + a.tiles_per_block, a.tiles);
+  const int per_img = a.tiles_h * a.tiles_w;
+  const int ty = threadIdx.x / VT_W, tx = threadIdx.x % VT_W;
+  int cur_n = t0 < t1 ? t0 / per_img : 0;
+  for (int tile = t0; tile < t1; ++tile) {
+    const int n = tile / per_img, rem = tile - n * per_img;
+    const int r0 = (rem / a.tiles_w) * VT_H, c0 = (rem % a.tiles_w) * VT_W;
+    if (n != cur_n) {   // (block-uniform) the block moves on to another image: hand in the counts of the one it leaves
+      __syncthreads();
+      for (int i = threadIdx.x; i < C; i += 256)
+        if (cls[i]) atomicAdd(&a.count[cur_n * C + i], (int)cls[i]);
+      __syncthreads();
+      for (int i = threadIdx.x; i < C; i += 256) cls[i] = 0u;
+      cur_n = n;
+    }
+    const int oh = r0 + ty, ow = c0 + tx;
+    const bool inside = oh < p.Ho && ow < p.Wo;
+    const long m = ((long)n * p.Ho + oh) * p.Wo + ow;
+    bool eligible = false;
+    if (inside) {
+      const int t = (int)(long)target[m];                  // the criterion's reading of a label (loss.hip: load_target)
+      eligible = t != a.ignore_index && (pl_in_mask(a.unl_lo, a.unl_hi, t) || (a.unl_value >= 0 && t == a.unl_value));
+    }
+    // (a barrier as well: the previous tile's readers are done with the patch, the cls reset above is visible)
+    const bool any = __syncthreads_or(eligible);
+    if (!any) {   // (block-uniform) nothing to label in this tile
+      if (inside) {
+        a.cls_map[m] = 255;
+        a.conf_map[m] = 0.f;
+      }
+      continue;
+    }
+    int ph0, ph1, pw0, pw1, tmp;
+    float ftmp;
+    src_index(r0, p.sh, p.H, ph0, tmp, ftmp);
+    src_index(min(r0 + VT_H, p.Ho) - 1, p.sh, p.H, tmp, ph1, ftmp);
+    src_index(c0, p.sw, p.W, pw0, tmp, ftmp);
+    src_index(min(c0 + VT_W, p.Wo) - 1, p.sw, p.W, tmp, pw1, ftmp);
+    const int ph = ph1 - ph0 + 1, pw = pw1 - pw0 + 1;
+    const bool staged = (long)ph * pw * CP <= (long)a.patch_cap;
+    const float* const img = p.x + (long)n * p.H * p.W * p.ldx;
+    if (staged) {
+      const int rowf = pw * C;
+      for (int e = threadIdx.x; e < ph * rowf; e += 256) {
+        const int r = e / rowf, j = e - r * rowf, px = j / C, c = j - px * C;
+        patch[(r * pw + px) * CP + c] = img[((long)(ph0 + r) * p.W + pw0 + px) * p.ldx + c];
+      }
+      __syncthreads();
+    }
+    if (!inside) continue;
+    int best = 255;
+    float conf = 0.f;
+    if (eligible) {
+      int h0, h1, w0, w1;
+      float lh, lw;
+      src_index(oh, p.sh, p.H, h0, h1, lh);
+      src_index(ow, p.sw, p.W, w0, w1, lw);
+      const float w00 = (1.f - lh) * (1.f - lw), w01 = (1.f - lh) * lw, w10 = lh * (1.f - lw), w11 = lh * lw;
+      if (staged) {
+        const float* q00 = patch + ((h0 - ph0) * pw + (w0 - pw0)) * CP;
+        const float* q01 = patch + ((h0 - ph0) * pw + (w1 - pw0)) * CP;
+        const float* q10 = patch + ((h1 - ph0) * pw + (w0 - pw0)) * CP;
+        const float* q11 = patch + ((h1 - ph0) * pw + (w1 - pw0)) * CP;
+        pl_pixel(q00, q01, q10, q11, w00, w01, w10, w11, C, a.cand_lo, a.cand_hi, best, conf);
+      } else {
+        const float* q00 = img + ((long)h0 * p.W + w0) * p.ldx;
+        const float* q01 = img + ((long)h0 * p.W + w1) * p.ldx;
+        const float* q10 = img + ((long)h1 * p.W + w0) * p.ldx;
+        const float* q11 = img + ((long)h1 * p.W + w1) * p.ldx;
+        pl_pixel(q00, q01, q10, q11, w00, w01, w10, w11, C, a.cand_lo, a.cand_hi, best, conf);
+      }
+      atomicAdd(&cls[best], 1u);
+    }
+    a.cls_map[m] = (unsigned char)best;
+    a.conf_map[m] = conf;
+  }
+  __syncthreads();
+  if (t0 < t1)
+    for (int i = threadIdx.x; i < C; i += 256)
+      if (cls[i]) atomicAdd(&a.count[cur_n * C + i], (int)cls[i]);
+}
+
+// the candidate mask names at least one class and none at or beyond C
+static bool pl_mask_ok(unsigned long long lo, unsigned long long hi, int C) {
+  if (!(lo | hi)) return false;
+  if (C < 64) return !hi && !(lo >> C);
+  return C == 128 || !(hi >> (C - 64));
+}
+
+extern "C" int zs3_pl_candidates(const float* scores, int ld, int N, int H, int W, int C, const void* target,
+                                 int target_is_i64, int Ho, int Wo, unsigned long long cand_lo, unsigned long long cand_hi,
+                                 unsigned long long unl_lo, unsigned long long unl_hi, int unlabelled_value,
+                                 int ignore_index, unsigned char* cls_map, float* conf_map, int* count, void* stream) {
+  if (C < 1 || C > 128 || N < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || ld < C) return -1;
+  if (!scores || !target || !cls_map || !conf_map || !count || !pl_mask_ok(cand_lo, cand_hi, C)) return -1;
+  PlArgs a;
+  a.r = make_resize(scores, ld, nullptr, 0, N, H, W, Ho, Wo, C, 0);
+  a.cand_lo = cand_lo; a.cand_hi = cand_hi; a.unl_lo = unl_lo; a.unl_hi = unl_hi;
+  a.cls_map = cls_map; a.conf_map = conf_map; a.count = count;
+  a.unl_value = unlabelled_value;
+  a.ignore_index = ignore_index;
+  a.tiles_h = (Ho + VT_H - 1) / VT_H;
+  a.tiles_w = (Wo + VT_W - 1) / VT_W;
+  const long tiles = (long)N * a.tiles_h * a.tiles_w;
+  if (tiles >= (1L << 31) || (long)N * C >= (1L << 31)) return -1;
+  a.tiles = (int)tiles;
+  const int blocks = (int)(tiles < 4 * VAL_MAX_BLOCKS ? tiles : 4 * VAL_MAX_BLOCKS);
+  a.tiles_per_block = (int)((tiles + blocks - 1) / blocks);
+  const int nblk = (int)((tiles + a.tiles_per_block - 1) / a.tiles_per_block);
+  const size_t fixed = (size_t)C * sizeof(unsigned);
+  const size_t want = (size_t)val_patch_extent(a.r.sh, VT_H, H) * val_patch_extent(a.r.sw, VT_W, W) * (C | 1) * sizeof(float);
+  const size_t budget = 64 * 1024 - 128;
+  a.patch_cap = fixed + want <= budget ? (int)(want / sizeof(float)) : 0;
+  const size_t lds = fixed + (size_t)a.patch_cap * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(val_zero_kernel, dim3((N * C + 255) / 256 > 64 ? 64 : (N * C + 255) / 256), dim3(256), 0, st, count, N * C);
+  if (target_is_i64)
+    hipLaunchKernelGGL(pl_candidates_kernel<long>, dim3(nblk), dim3(256), lds, st, a, (const long*)target);
+  else
+    hipLaunchKernelGGL(pl_candidates_kernel<float>, dim3(nblk), dim3(256), lds, st, a, (const float*)target);
+  return ZS3_LAUNCH_CHECK();
+}
+
+// ---- selection
+constexpr int PL_BINS = 256, PL_PASSES = 4;   // 8-bit digits of the 32-bit pattern, most significant first
+
+struct PlSel {
+  const unsigned* conf;          // conf_map read as bit patterns (no arithmetic touches it: denormals stay what they are)
+  const unsigned char* cls;
+  const int* count;
+  unsigned* hist;                // workspace: [buckets][PL_BINS]
+  unsigned* prefix;              // [buckets] the bits of t settled so far (right-aligned)
+  unsigned* krem;                // [buckets] the rank still to be found inside the prefix; 0: the bucket keeps nothing
+  unsigned long long cand_lo, cand_hi;
+  int N, C, P;                   // P: pixels per image
+  int group;                     // 0: bucket = (image, class), index n*C + c;  1: bucket = image, index n
+  int pass, shift, nslots, lds_hist, per_block;
+  double top_percent;
+};
+
+// per class of image n: the bucket's prefix and remaining rank, and the row of the block's LDS histogram
+__device__ __forceinline__ void pl_load_buckets(const PlSel& a, int n, unsigned* pre, unsigned* rank, int* slot) {
+  for (int c = threadIdx.x; c < a.C; c += blockDim.x) {
+    const bool is_cand = pl_in_mask(a.cand_lo, a.cand_hi, c);
+    const int b = a.group ? n : n * a.C + c;
+    pre[c] = is_cand ? a.prefix[b] : 0u;
+    rank[c] = is_cand ? a.krem[b] : 0u;
+    slot[c] = !is_cand ? -1 : (a.group ? 0 : pl_slot(a.cand_lo, a.cand_hi, c));
+  }
+}
+
+__global__ __launch_bounds__(256) void pl_hist_kernel(const PlSel a) {
+  extern __shared__ unsigned pl_hist_lds[];      // [nslots][PL_BINS] when lds_hist
+  __shared__ unsigned pre[128], rank[128];
+  __shared__ int slot[128], slot_cls[128];
+  const int n = blockIdx.y;
+  pl_load_buckets(a, n, pre, rank, slot);
+  if (a.lds_hist)
+    for (int i = threadIdx.x; i < a.nslots * PL_BINS; i += 256) pl_hist_lds[i] = 0u;
+  __syncthreads();
+  for (int c = threadIdx.x; c < a.C; c += 256)
+    if (slot[c] >= 0 && !a.group) slot_cls[slot[c]] = c;
+  const long base = (long)n * a.P;
+  const int i0 = blockIdx.x * a.per_block, i1 = min(i0 + a.per_block, a.P);
+  for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+    const int c = a.cls[base + i];
+    if (c >= a.C) continue;                       // 255: not eligible
+    const int s = slot[c];
+    if (s < 0) continue;
+    const unsigned bits = a.conf[base + i];
+    if (a.pass > 0 && (rank[c] == 0u || (bits >> (a.shift + 8)) != pre[c])) continue;
+    const unsigned d = (bits >> a.shift) & (PL_BINS - 1);
+    if (a.lds_hist) atomicAdd(&pl_hist_lds[s * PL_BINS + d], 1u);
+    else atomicAdd(&a.hist[(long)(a.group ? n : n * a.C + c) * PL_BINS + d], 1u);
+  }
+  if (!a.lds_hist) return;
+  __syncthreads();
+  for (int i = threadIdx.x; i < a.nslots * PL_BINS; i += 256) {
+    const unsigned v = pl_hist_lds[i];
+    if (v) atomicAdd(&a.hist[(long)(a.group ? n : n * a.C + slot_cls[i / PL_BINS]) * PL_BINS + (i % PL_BINS)], v);
+  }
+}
+
+// one wave per bucket: lane l owns bins 4l .. 4l+3.  Finds the digit d with #{bins > d} < k <= #{bins >= d}, appends it to the
+// prefix, takes #{bins > d} off the rank and clears the histogram.  Pass 0 computes k; the last pass writes the threshold.
+__global__ __launch_bounds__(64) void pl_scan_kernel(const PlSel a, unsigned* threshold) {
+  __shared__ unsigned found[2];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  u32x4* const h = reinterpret_cast<u32x4*>(a.hist + (long)b * PL_BINS);
+  const u32x4 v = h[lane];
+  h[lane] = u32x4{0u, 0u, 0u, 0u};
+  unsigned k;
+  if (a.pass == 0) {
+    int m = 0;
+    if (a.group) {
+      for (int c = lane; c < a.C; c += 64) m += a.count[b * a.C + c];
+      for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
+    } else {
+      m = a.count[b];
+    }
+    const double want = ceil((double)m * a.top_percent / 100.0);
+    k = (unsigned)(want < (double)m ? want : (double)m);
+  } else {
+    k = a.krem[b];
+  }
+  if (lane == 0) {
+    found[0] = a.pass == 0 ? 0u : a.prefix[b];
+    found[1] = 0u;
+  }
+  __syncthreads();
+  if (k > 0u) {
+    const unsigned own = v[0] + v[1] + v[2] + v[3];
+    unsigned incl = own;   // sum over lanes >= this one
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned t = __shfl_down(incl, o, 64);
+      if (lane + o < 64) incl += t;
+    }
+    unsigned above = incl - own;
+    if (above < k && k <= incl) {   // exactly one lane (1 <= k <= number of values counted)
+      int d = 3;
+      while (above + v[d] < k) {
+        above += v[d];
+        --d;
+      }
+      found[0] = ((a.pass == 0 ? 0u : a.prefix[b]) << 8) | (unsigned)(4 * lane + d);
+      found[1] = k - above;
+    }
+  }
+  __syncthreads();
+  if (lane == 0) {
+    a.prefix[b] = found[0];
+    a.krem[b] = found[1];
+  }
+  if (a.pass == PL_PASSES - 1) {
+    const unsigned t = found[1] ? found[0] : 0u;
+    if (a.group) {
+      for (int c = lane; c < a.C; c += 64) threshold[b * a.C + c] = pl_in_mask(a.cand_lo, a.cand_hi, c) ? t : 0u;
+    } else if (lane == 0) {
+      threshold[b] = t;
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pl_final_kernel(const PlSel a, const T* target, T* labels, int* selected, int ignore_index,
+                                                      unsigned long long* totals) {
+  __shared__ unsigned pre[128], rank[128], sel[128];
+  __shared__ int slot[128];
+  const int n = blockIdx.y;
+  pl_load_buckets(a, n, pre, rank, slot);
+  for (int c = threadIdx.x; c < 128; c += 256) sel[c] = 0u;
+  __syncthreads();
+  const long base = (long)n * a.P;
+  const int i0 = blockIdx.x * a.per_block, i1 = min(i0 + a.per_block, a.P);
+  for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+    const int c = a.cls[base + i];
+    T out;
+    if (c >= a.C) {
+      out = target[base + i];
+    } else {
+      const bool keep = rank[c] != 0u && a.conf[base + i] >= pre[c];
+      out = keep ? (T)c : (T)ignore_index;
+      if (keep) atomicAdd(&sel[c], 1u);
+    }
+    labels[base + i] = out;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < a.C; c += 256)
+    if (sel[c]) atomicAdd(&selected[n * a.C + c], (int)sel[c]);
+  if (totals)   // running sums over the calls: [0][c] += count, [1][c] += selected (integers: exact in any order)
+    for (int c = threadIdx.x; c < a.C; c += 256) {
+      const int cnt = blockIdx.x == 0 ? a.count[n * a.C + c] : 0;
+      if (cnt) atomicAdd(&totals[c], (unsigned long long)cnt);
+      if (sel[c]) atomicAdd(&totals[a.C + c], (unsigned long long)sel[c]);
+    }
+}
+
+__global__ void pl_clear_kernel(unsigned* ws, long nws, int* selected, int nsel) {
+  const long step = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nws; i += step) ws[i] = 0u;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nsel; i += step) selected[i] = 0;
+}
+
+extern "C" long zs3_pl_ws_bytes(int N, int C) {
+  if (N < 1 || C < 1 || C > 128) return -1;
+  return (long)N * C * (PL_BINS + 2) * (long)sizeof(unsigned);
+}
+
+extern "C" int zs3_pl_select(const float* conf_map, const unsigned char* cls_map, const void* target, int target_is_i64,
+                             int N, int Ho, int Wo, int C, unsigned long long cand_lo, unsigned long long cand_hi,
+                             const int* count, double top_percent, int group, int ignore_index, void* labels,
+                             int* selected, float* threshold, void* totals, void* ws, void* stream) {
+  if (C < 1 || C > 128 || N < 1 || N > 65535 || Ho < 1 || Wo < 1 || (long)Ho * Wo >= (1L << 31) || (long)N * C >= (1L << 23)) return -1;
+  if (!conf_map || !cls_map || !target || !count || !labels || !selected || !threshold || !ws) return -1;
+  if (!pl_mask_ok(cand_lo, cand_hi, C) || (group != 0 && group != 1) || !(top_percent >= 0.0 && top_percent <= 100.0)) return -1;
+  if (((uintptr_t)ws & 15u) != 0) return -1;   // (the scan reads a bucket's histogram 16 bytes per lane)
+  const long nb = (long)N * C;
+  PlSel a;
+  a.conf = reinterpret_cast<const unsigned*>(conf_map);
+  a.cls = cls_map;
+  a.count = count;
+  a.hist = static_cast<unsigned*>(ws);
+  a.prefix = a.hist + nb * PL_BINS;
+  a.krem = a.prefix + nb;
+  a.cand_lo = cand_lo; a.cand_hi = cand_hi;
+  a.N = N; a.C = C; a.P = Ho * Wo;
+  a.group = group;
+  a.nslots = group ? 1 : __builtin_popcountll(cand_lo) + __builtin_popcountll(cand_hi);
+  const size_t hist_lds = (size_t)a.nslots * PL_BINS * sizeof(unsigned);
+  a.lds_hist = hist_lds <= 60 * 1024;
+  a.top_percent = top_percent;
+  int bx = (a.P + 256 * 16 - 1) / (256 * 16);
+  if (bx > 128) bx = 128;
+  a.per_block = (a.P + bx - 1) / bx;
+  bx = (a.P + a.per_block - 1) / a.per_block;
+  const dim3 grid(bx, N);
+  const int buckets = group ? N : (int)nb;
+  hipStream_t st = (hipStream_t)stream;
+  const long nws = nb * (PL_BINS + 2);
+  hipLaunchKernelGGL(pl_clear_kernel, dim3((int)((nws + 255) / 256 > 256 ? 256 : (nws + 255) / 256)), dim3(256), 0, st,
+                     a.hist, nws, selected, (int)nb);
+  for (int pass = 0; pass < PL_PASSES; ++pass) {
+    a.pass = pass;
+    a.shift = 32 - 8 * (pass + 1);
+    hipLaunchKernelGGL(pl_hist_kernel, grid, dim3(256), a.lds_hist ? hist_lds : 0, st, a);
+    hipLaunchKernelGGL(pl_scan_kernel, dim3(buckets), dim3(64), 0, st, a, reinterpret_cast<unsigned*>(threshold));
+  }
+  if (target_is_i64)
+    hipLaunchKernelGGL(pl_final_kernel<long>, grid, dim3(256), 0, st, a, (const long*)target, (long*)labels, selected, ignore_index,
+                       (unsigned long long*)totals);
+  else
+    hipLaunchKernelGGL(pl_final_kernel<float>, grid, dim3(256), 0, st, a, (const float*)target, (float*)labels, selected, ignore_index,
+                       (unsigned long long*)totals);
+  return ZS3_LAUNCH_CHECK();
+}

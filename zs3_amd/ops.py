@@ -828,6 +828,161 @@ def val_ce_confusion(scores, target, conf, weight=None, ignore_index=255, batch=
     return loss_ws
 
 
+# ------------------------------------------------------------------------------------------- pseudo-labelling (ZS5)
+PL_GROUPS = {"image_class": 0, "image": 1}
+
+
+def class_mask(classes):
+    """(lo, hi): the set of class indices 0 .. 127 as two 64-bit masks (bit c of lo, bit c - 64 of hi), the form in which class sets
+    travel to zs3_pl_candidates / zs3_pl_select"""
+    lo = hi = 0
+    for c in classes:
+        c = int(c)
+        if not 0 <= c < 128:
+            raise ValueError(f"class_mask: class {c} outside 0 .. 127")
+        if c < 64:
+            lo |= 1 << c
+        else:
+            hi |= 1 << (c - 64)
+    return lo, hi
+
+
+def pl_keep_count(m, p):
+    """k of a bucket with m eligible pixels at top_percent p: min(m, ceil(m * p / 100)) in double -- the arithmetic of the
+    device (pl_scan_kernel)"""
+    import math
+    return min(int(m), int(math.ceil(float(int(m)) * float(p) / 100.0)))
+
+
+def pl_ws(n, c, device):
+    """workspace of pl_select (zs3_pl_ws_bytes(N, C) bytes); the call clears it itself"""
+    nbytes = lib().zs3_pl_ws_bytes(I(n), I(c))
+    if nbytes < 0:
+        raise ValueError("pl_ws: N >= 1 and 1 <= C <= 128 expected")
+    return torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=device)
+
+
+def _pl_sets(c, candidates, unlabelled, unlabelled_value):
+    cand = sorted({int(k) for k in candidates})
+    if not cand or cand[0] < 0 or cand[-1] >= c:
+        raise ValueError("pseudo-labelling: a non-empty set of candidate classes in 0 .. C - 1 expected")
+    unl = class_mask(cand if unlabelled is None else unlabelled)
+    uv = -1 if unlabelled_value is None else int(unlabelled_value)
+    if unlabelled_value is not None and uv < 0:
+        raise ValueError("pseudo-labelling: unlabelled_value is a non-negative label value")
+    return class_mask(cand), unl, uv
+
+
+def _pl_target(name, target, n):
+    if target.dtype not in (torch.float32, torch.int64) or not target.is_contiguous():
+        raise TypeError(f"{name}: a contiguous float32 / int64 target expected")
+    if target.dim() != 3 or target.shape[0] != n:
+        raise ValueError(f"{name}: target [N, H, W] expected")
+
+
+def pl_candidates(scores, target, candidates, unlabelled=None, unlabelled_value=None, ignore_index=255, cls_map=None,
+                  conf_map=None, count=None):
+    """zs3_pl_candidates: scores fp32 [N, h, w, C] (NHWC, pixel stride >= C), target float32 / int64 [N, H, W].  A pixel whose
+    label is in `unlabelled` (default: the candidates) or equals `unlabelled_value`, and is not ignore_index, is eligible: it gets
+    c* = the first argmax over `candidates` of the scores sampled at its position (the values of bilinear_fwd) and the softmax
+    probability of c* over all classes.  -> (cls_map uint8 [N, H, W], 255 = not eligible; conf_map fp32 [N, H, W]; count int32
+    [N, C]).  Nothing here synchronises or launches outside the library."""
+    if scores.dim() != 4:
+        raise ValueError("pl_candidates: scores [N, h, w, C] expected")
+    n, h, w_, c = scores.shape
+    if scores.dtype != torch.float32:
+        raise TypeError("pl_candidates: fp32 scores expected")
+    _pl_target("pl_candidates", target, n)
+    if not 1 <= c <= 128:
+        raise ValueError("pl_candidates: 1 <= C <= 128")
+    cand, unl, uv = _pl_sets(c, candidates, unlabelled, unlabelled_value)
+    shape, dev = tuple(target.shape), scores.device
+    if cls_map is None:
+        cls_map = torch.empty(shape, dtype=torch.uint8, device=dev)
+    if conf_map is None:
+        conf_map = torch.empty(shape, dtype=torch.float32, device=dev)
+    if count is None:
+        count = torch.empty((n, c), dtype=torch.int32, device=dev)
+    _pl_maps("pl_candidates", cls_map, conf_map, count, shape, c)
+    require_gpu(scores, target, cls_map, conf_map, count)     # (after the argument checks: those need no device)
+    check(lib().zs3_pl_candidates(P(scores), I(_check_nhwc(scores)), I(n), I(h), I(w_), I(c), P(target),
+                                  I(int(target.dtype == torch.int64)), I(shape[1]), I(shape[2]), cand[0], cand[1], unl[0], unl[1],
+                                  I(uv), I(ignore_index), P(cls_map), P(conf_map), P(count), stream()), "zs3_pl_candidates")
+    return cls_map, conf_map, count
+
+
+def _pl_maps(name, cls_map, conf_map, count, shape, c):
+    if cls_map.dtype != torch.uint8 or tuple(cls_map.shape) != shape or not cls_map.is_contiguous():
+        raise ValueError(f"{name}: cls_map is a contiguous uint8 [N, H, W] tensor")
+    if conf_map.dtype != torch.float32 or tuple(conf_map.shape) != shape or not conf_map.is_contiguous():
+        raise ValueError(f"{name}: conf_map is a contiguous fp32 [N, H, W] tensor")
+    if count.dtype != torch.int32 or tuple(count.shape) != (shape[0], c) or not count.is_contiguous():
+        raise ValueError(f"{name}: count is a contiguous int32 [N, C] tensor")
+
+
+def pl_select(cls_map, conf_map, count, target, candidates, top_percent, group="image_class", ignore_index=255, labels=None,
+              selected=None, threshold=None, ws=None, totals=None):
+    """zs3_pl_select on the maps of pl_candidates: per bucket -- (image, c*) for group "image_class", the image for "image" -- of m
+    eligible pixels keep the k = pl_keep_count(m, top_percent) most confident ones, exactly, with every pixel tied with the k-th
+    kept too (conf >= t).  -> (labels like target: target where not eligible, c* where kept, ignore_index otherwise; selected
+    int32 [N, C]; threshold fp32 [N, C]).  totals: int64 [2, C] or None, accumulated (count and selected summed over the images).
+    No host synchronisation."""
+    if count.dim() != 2:
+        raise ValueError("pl_select: count is int32 [N, C]")
+    n, c = count.shape
+    _pl_target("pl_select", target, n)
+    if not 1 <= c <= 128:
+        raise ValueError("pl_select: 1 <= C <= 128")
+    if group not in PL_GROUPS:
+        raise ValueError(f"pl_select: group is one of {sorted(PL_GROUPS)}, not {group!r}")
+    p = float(top_percent)
+    if not 0.0 <= p <= 100.0:
+        raise ValueError("pl_select: top_percent in [0, 100] expected")
+    cand, _, _ = _pl_sets(c, candidates, None, None)
+    shape, dev = tuple(target.shape), target.device
+    _pl_maps("pl_select", cls_map, conf_map, count, shape, c)
+    if labels is None:
+        labels = torch.empty_like(target)
+    if selected is None:
+        selected = torch.empty((n, c), dtype=torch.int32, device=dev)
+    if threshold is None:
+        threshold = torch.empty((n, c), dtype=torch.float32, device=dev)
+    if ws is None:
+        ws = pl_ws(n, c, dev)
+    if labels.dtype != target.dtype or tuple(labels.shape) != shape or not labels.is_contiguous():
+        raise ValueError("pl_select: labels has the type and shape of target")
+    if selected.dtype != torch.int32 or tuple(selected.shape) != (n, c) or not selected.is_contiguous():
+        raise ValueError("pl_select: selected is a contiguous int32 [N, C] tensor")
+    if threshold.dtype != torch.float32 or tuple(threshold.shape) != (n, c) or not threshold.is_contiguous():
+        raise ValueError("pl_select: threshold is a contiguous fp32 [N, C] tensor")
+    if totals is not None and (totals.dtype != torch.int64 or tuple(totals.shape) != (2, c) or not totals.is_contiguous()):
+        raise ValueError("pl_select: totals is a contiguous int64 [2, C] tensor")
+    if ws.numel() * ws.element_size() < lib().zs3_pl_ws_bytes(I(n), I(c)):
+        raise ValueError("pl_select: the workspace is smaller than zs3_pl_ws_bytes(N, C)")
+    require_gpu(cls_map, conf_map, count, target, labels, selected, threshold, ws, totals)
+    check(lib().zs3_pl_select(P(conf_map), P(cls_map), P(target), I(int(target.dtype == torch.int64)), I(n), I(shape[1]),
+                              I(shape[2]), I(c), cand[0], cand[1], P(count), p, I(PL_GROUPS[group]), I(ignore_index), P(labels),
+                              P(selected), P(threshold), P(totals), P(ws), stream()), "zs3_pl_select")
+    return labels, selected, threshold
+
+
+def pseudo_label(scores, target, candidates, top_percent, group="image_class", unlabelled=None, unlabelled_value=None,
+                 ignore_index=255, labels=None, cls_map=None, conf_map=None, count=None, selected=None, threshold=None, ws=None,
+                 totals=None):
+    """pl_candidates + pl_select: the self-training label maps of one batch from its low-resolution class scores.  -> (labels,
+    stats) with stats = {"cls_map", "conf_map", "count", "selected", "threshold"}.  Every output and the workspace may be passed
+    preallocated (a step that is to be recorded allocates nothing between its launches)."""
+    if group not in PL_GROUPS:
+        raise ValueError(f"pseudo_label: group is one of {sorted(PL_GROUPS)}, not {group!r}")
+    if not 0.0 <= float(top_percent) <= 100.0:
+        raise ValueError("pseudo_label: top_percent in [0, 100] expected")
+    cls_map, conf_map, count = pl_candidates(scores, target, candidates, unlabelled, unlabelled_value, ignore_index,
+                                             cls_map=cls_map, conf_map=conf_map, count=count)
+    labels, selected, threshold = pl_select(cls_map, conf_map, count, target, candidates, top_percent, group, ignore_index,
+                                            labels=labels, selected=selected, threshold=threshold, ws=ws, totals=totals)
+    return labels, {"cls_map": cls_map, "conf_map": conf_map, "count": count, "selected": selected, "threshold": threshold}
+
+
 # ------------------------------------------------------------------------------------------- misc
 def dropout(x, p, seed, out=None, row_idx=None, seed_dev=None):
     m, c, ld = _rows(x)
